@@ -38,6 +38,17 @@ launch stream.
 cpu_baseline (rank 0, every N, after the timed region): the reference's own fd_ed25519_verify (AVX-512
 IFMA build, compiled from the reference sources into oracle/_ref/) on a
 bounded 65536-record sample of the same batch, one pinned thread per core.
+
+A plain run (bench.py --gpus 1 --steps N --warmup W) does what the headline
+figure needs and no more: it makes the batch, warms up, times the N steps
+and prints the line (metric, value, unit, ms_per_step, ...).  --full adds
+every other leg to the same line, after the timed region: the roofline leg
+(and its check of the timed verdicts against a whole-batch pass), the
+pipeline figures, cpu_baseline, the config-4 sub-object and the tile leg
+(c2), and config 4's own PCIe-inclusive leg, roofline batch and CPU tile
+baseline.  --dump-outputs DIR saves what the last timed step computed
+(dump_outputs()); the inputs are seeded, so two builds run with the same
+arguments can be compared output for output.
 """
 import argparse
 import json
@@ -241,6 +252,107 @@ def cpu_baseline(sigs, pubs, pool, moff, msz, gpu_codes, threads, target_s):
             "codes_match": bool(np.array_equal(ref_codes, gpu_codes))}
 
 
+def full_legs(args, cfg, rank, n, chunk, msg_sz, batch, v, step, whole, sync_all, codes, gcodes, c):
+    """--full, c1/c2/c3/c5, after the timed steps: the roofline leg (every
+    rank), then on rank 0 the roofline and pipeline figures and the CPU
+    baseline.  c holds the timed steps' codes.  Returns the line's
+    "roofline", "pipeline" and "cpu_baseline" entries."""
+    import torch
+    timed_codes, timed_gcodes = codes.clone(), gcodes.clone()
+    # roofline leg: the whole batch through one context with HIP events around
+    # every launch (timing mode), so each k_verify_dsm runs alone on the GPU;
+    # its verdicts must equal the timed multi-context steps'
+    v.set_timing(True)
+    for _ in range(max(1, min(args.steps, 3))):
+        step(whole)
+    sync_all()
+    prep_ms, dsm_ms, launches = v.get_timing()
+    v.set_timing(False)
+    assert torch.equal(codes, timed_codes) and torch.equal(gcodes, timed_gcodes), "contexts != whole batch"
+    if rank != 0:
+        return None
+    reached_dsm = int(np.isin(c, (0, -3)).sum())          # passed every pre-check
+    launches_per_step = -(-n // chunk)
+    dsm_avg_ms = dsm_ms / max(launches, 1)
+    prep_avg_ms = prep_ms / max(launches, 1)
+    units_per_launch = reached_dsm / launches_per_step
+    # T int32-ops/s per GPU: SURVEY 8(d)'s per-unit W (the reference
+    # algorithm's work), and the kernel's own smaller half-size work
+    achieved = units_per_launch * W_DSM / (dsm_avg_ms * 1e-3) / 1e12
+    peak = PEAK_OPS / 1e12
+    # whole pipeline (prep + DSM): the prep work (decodes + hash) for every
+    # signature, the DSM work only for those that pass the pre-checks
+    pipe_s = (prep_avg_ms + dsm_avg_ms) * 1e-3 * max(launches_per_step, 1)
+    w_prep = w_total(msg_sz) - W_DSM
+    pipeline_frac = (n * w_prep + reached_dsm * W_DSM) / pipe_s / PEAK_OPS
+
+    # HBM-side bytes per k_verify_dsm launch from the committed rocprofv3 PMC
+    # passes of this same command (FETCH_SIZE x2 per the gfx950 note + WRITE_SIZE)
+    issue = issue_roofline(dsm_avg_ms, units_per_launch)
+    traffic, traffic_src = None, None
+    pmc = os.path.join(REPO, "profiles", PMC_SUMMARY)
+    if cfg == "c2" and n == (1 << 20) and os.path.exists(pmc):
+        with open(pmc) as f:
+            traffic = json.load(f)["kernels"]["k_verify_dsm"]["derived"]["hbm_side_bytes_per_launch"]
+        traffic_src = f"profiles/{PMC_SUMMARY}: FETCH_SIZE*2 + WRITE_SIZE of k_verify_dsm (rocprofv3 --pmc)"
+    ingest_bytes = 64 + 32 + msg_sz + 8                   # sig, pub, msg, off/sz per signature
+    ingest_gbps = n / launches_per_step * ingest_bytes / (prep_avg_ms * 1e-3) / 1e9
+
+    cpu = None
+    if not args.no_cpu_baseline:          # rank 0, after every rank's timed region
+        k = min(65536, n)
+        idx = slice(0, k)
+        sigs = batch.sigs[idx].cpu().numpy(); pubs = batch.pubs[idx].cpu().numpy()
+        moff = batch.msg_off[idx].cpu().numpy().view(np.uint32)
+        msz = batch.msg_sz[idx].cpu().numpy().view(np.uint32)
+        lo = int(moff.min()); hi = int((moff.astype(np.int64) + msz).max())
+        pool = batch.pool[lo:hi].cpu().numpy()
+        threads = max(1, min(args.cpu_threads, os.cpu_count() or 1))
+        cpu = cpu_baseline(sigs, pubs, pool, moff - lo, msz, c[idx], threads, args.cpu_seconds)
+        cpu["sample"] = cpu.get("sample", "") + f" [{cfg}]"
+    return {
+        "roofline": dict(issue or {}, **{
+                     "kernel": "k_verify_dsm", "traffic": traffic, "traffic_unit": "bytes/launch",
+                     "traffic_source": traffic_src, "units_per_launch": round(units_per_launch),
+                     "avg_launch_ms": round(dsm_avg_ms, 4),
+                     "ref_work_rate_vs_peak": round(achieved / peak, 4),
+                     "ref_work_note": "SURVEY 8(d)'s W (the reference algorithm's full-length-scalar work, "
+                                      f"{round(W_DSM)} int32-op equivalents per unit) x units / time / 78.6 "
+                                      "Tops/s: a speed-up figure over the reference algorithm, NOT a "
+                                      "utilisation (the half-size kernel does 17% less work, so it can pass 1)",
+                     "timing_leg": "after the timed steps: the whole batch through one context, HIP events "
+                                   "around each launch, each k_verify_dsm alone on the GPU"}),
+        "pipeline": {"prep_ms": round(prep_avg_ms, 4), "dsm_ms": round(dsm_avg_ms, 4),
+                     "prep_issue_slot_util": prep_issue_util(),
+                     "w_total_per_verify": round(w_total(msg_sz)),
+                     "ref_work_rate_vs_peak": round(pipeline_frac, 4),
+                     "ref_work_note": "prep work (decodes + hash) for every signature, DSM work for those "
+                                      "reaching it, at 8(d)'s W, over the prep + DSM time: a speed-up figure "
+                                      "over the reference algorithm, not a utilisation",
+                     "ingest_GBps": round(ingest_gbps, 2), "ingest_bytes_per_sig": ingest_bytes},
+        "cpu_baseline": cpu,
+    }
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: the arrays a caller of the timed path received from
+    its last step, as d/<name>.npy in float32 (verdict codes, bits and sizes
+    are small integers, exact in float32).  At most DUMP_MAX_BYTES in all: an
+    array over its share is cut to a fixed, seeded sample of its elements (in
+    index order), the same for every run with the same shapes."""
+    os.makedirs(d, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(len(arrays), 1) // 4
+    for name, a in arrays.items():
+        a = np.asarray(a).reshape(-1)
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(0x5eed0d07).choice(a.size, share, replace=False))
+            a = a[idx]
+        np.save(os.path.join(d, name + ".npy"), a.astype(np.float32))
+
+
 _JSON_FD = [1]
 COLL_DEV = None          # device of the tensors the collectives reduce (GPU for RCCL, CPU for gloo)
 
@@ -263,6 +375,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every secondary leg and attach it to the line: the roofline "
+                         "leg and pipeline figures, cpu_baseline, the c4 sub-object and the tile leg (c2), and c4's "
+                         "PCIe-inclusive leg, roofline batch and CPU tile baseline (--no-c4, --no-tile and "
+                         "--no-cpu-baseline drop single legs of a --full run)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 saves the outputs of the last timed step as DIR/<name>.npy (float32, at most 64 MB in "
+                         "all): codes and bitmap_bits (c1/c2/c3/c5; group_codes too for c3), frag_results and "
+                         "txn_sz (c4)")
     ap.add_argument("--config", default="c2", choices=["c1", "c2", "c3", "c4", "c5"],
                     help="BASELINE.json configs: c1 all-valid 2^20/GPU; c2 (default, the metric's config) "
                          "C2 mix 2^20/GPU; c3 one 32-B message x 2^22 keys/GPU as batch_single_msg "
@@ -307,7 +428,7 @@ def main():
                     help="nccl (RCCL over xGMI, one rank per GPU: the driver's N-GPU runs); gloo rehearses the "
                          "N>1 path with several ranks sharing one GPU (rank r on GPU r %% device_count)")
     args = ap.parse_args()
-    if args.config == "c4" or (args.config == "c2" and not args.no_c4):
+    if args.config == "c4" or (args.config == "c2" and args.full and not args.no_c4):
         # The reference runs each verify tile as its own process, each with the
         # HIP runtime's own hardware queues; here the tiles are threads of one
         # process, so give that process a queue per tile (HIP default 4).
@@ -418,30 +539,23 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t1 = time.perf_counter()
-    timed_codes, timed_gcodes = codes.clone(), gcodes.clone()
-    # roofline leg: the whole batch through one context with HIP events around
-    # every launch (timing mode), so each k_verify_dsm runs alone on the GPU;
-    # its verdicts must equal the timed multi-context steps'
-    v.set_timing(True)
-    for _ in range(max(1, min(args.steps, 3))):
-        step(whole)
-    sync_all()
-    prep_ms, dsm_ms, launches = v.get_timing()
-    v.set_timing(False)
-    assert torch.equal(codes, timed_codes) and torch.equal(gcodes, timed_gcodes), "contexts != whole batch"
     elapsed = t1 - t0
     if dist:
         t = torch.tensor([elapsed], dtype=torch.float64, device=COLL_DEV)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    # the timed steps' own outputs (the roofline leg of a --full run writes the same buffers again)
     c = codes.cpu().numpy()
+    bm = bitmap.cpu().numpy().view(np.uint64)
+    gc = gcodes.cpu().numpy()
     if args.dump_codes:                       # this rank's verdicts, for the shard-vs-whole-set checks
         np.save(f"{args.dump_codes}.{rank}.npy", c)
-    bm = bitmap.cpu().numpy().view(np.uint64)
     bits = np.unpackbits(bm.view(np.uint8), bitorder="little")[:n].astype(bool)
     assert np.array_equal(bits, c == 0), "bitmap != codes"
-    reached_dsm = int(np.isin(c, (0, -3)).sum())          # passed every pre-check
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict({"codes": c, "bitmap_bits": bits},
+                                             **({"group_codes": gc} if cfg == "c3" else {})))
     accept = float((c == 0).mean())
 
     if dist:
@@ -452,46 +566,9 @@ def main():
         n_all = n
     total = n_all * args.steps
     value = total / elapsed
-    launches_per_step = -(-n // chunk)
-    dsm_avg_ms = dsm_ms / max(launches, 1)
-    prep_avg_ms = prep_ms / max(launches, 1)
-    units_per_launch = reached_dsm / launches_per_step
-    # T int32-ops/s per GPU: SURVEY 8(d)'s per-unit W (the reference
-    # algorithm's work), and the kernel's own smaller half-size work
-    achieved = units_per_launch * W_DSM / (dsm_avg_ms * 1e-3) / 1e12
-    peak = PEAK_OPS / 1e12
-    # whole pipeline (prep + DSM): the prep work (decodes + hash) for every
-    # signature, the DSM work only for those that pass the pre-checks
-    pipe_s = (prep_avg_ms + dsm_avg_ms) * 1e-3 * max(launches_per_step, 1)
-    w_prep = w_total(msg_sz) - W_DSM
-    pipeline_frac = (n * w_prep + reached_dsm * W_DSM) / pipe_s / PEAK_OPS
-
-    # HBM-side bytes per k_verify_dsm launch from the committed rocprofv3 PMC
-    # passes of this same command (FETCH_SIZE x2 per the gfx950 note + WRITE_SIZE)
-    issue = issue_roofline(dsm_avg_ms, units_per_launch)
-    traffic, traffic_src = None, None
-    pmc = os.path.join(REPO, "profiles", PMC_SUMMARY)
-    if cfg == "c2" and n == (1 << 20) and os.path.exists(pmc):
-        with open(pmc) as f:
-            traffic = json.load(f)["kernels"]["k_verify_dsm"]["derived"]["hbm_side_bytes_per_launch"]
-        traffic_src = f"profiles/{PMC_SUMMARY}: FETCH_SIZE*2 + WRITE_SIZE of k_verify_dsm (rocprofv3 --pmc)"
-    ingest_bytes = 64 + 32 + msg_sz + 8                   # sig, pub, msg, off/sz per signature
-    ingest_gbps = n / launches_per_step * ingest_bytes / (prep_avg_ms * 1e-3) / 1e9
 
     out = None
     if rank == 0:
-        cpu = None
-        if not args.no_cpu_baseline:          # rank 0, after every rank's timed region
-            k = min(65536, n)
-            idx = slice(0, k)
-            sigs = batch.sigs[idx].cpu().numpy(); pubs = batch.pubs[idx].cpu().numpy()
-            moff = batch.msg_off[idx].cpu().numpy().view(np.uint32)
-            msz = batch.msg_sz[idx].cpu().numpy().view(np.uint32)
-            lo = int(moff.min()); hi = int((moff.astype(np.int64) + msz).max())
-            pool = batch.pool[lo:hi].cpu().numpy()
-            threads = max(1, min(args.cpu_threads, os.cpu_count() or 1))
-            cpu = cpu_baseline(sigs, pubs, pool, moff - lo, msz, c[idx], threads, args.cpu_seconds)
-            cpu["sample"] = cpu.get("sample", "") + f" [{cfg}]"
         out = {
             "metric": METRIC,
             "value": round(value, 1),
@@ -514,30 +591,14 @@ def main():
                        "parallelism": f"dp{world} (signature shards)",
                        "verify_contexts": len(ctxs)},
             "accept_rate": round(accept, 5),
-            "roofline": dict(issue or {}, **{
-                         "kernel": "k_verify_dsm", "traffic": traffic, "traffic_unit": "bytes/launch",
-                         "traffic_source": traffic_src, "units_per_launch": round(units_per_launch),
-                         "avg_launch_ms": round(dsm_avg_ms, 4),
-                         "ref_work_rate_vs_peak": round(achieved / peak, 4),
-                         "ref_work_note": "SURVEY 8(d)'s W (the reference algorithm's full-length-scalar work, "
-                                          f"{round(W_DSM)} int32-op equivalents per unit) x units / time / 78.6 "
-                                          "Tops/s: a speed-up figure over the reference algorithm, NOT a "
-                                          "utilisation (the half-size kernel does 17% less work, so it can pass 1)",
-                         "timing_leg": "after the timed steps: the whole batch through one context, HIP events "
-                                       "around each launch, each k_verify_dsm alone on the GPU"}),
-            "pipeline": {"prep_ms": round(prep_avg_ms, 4), "dsm_ms": round(dsm_avg_ms, 4),
-                         "prep_issue_slot_util": prep_issue_util(),
-                         "w_total_per_verify": round(w_total(msg_sz)),
-                         "ref_work_rate_vs_peak": round(pipeline_frac, 4),
-                         "ref_work_note": "prep work (decodes + hash) for every signature, DSM work for those "
-                                          "reaching it, at 8(d)'s W, over the prep + DSM time: a speed-up figure "
-                                          "over the reference algorithm, not a utilisation",
-                         "ingest_GBps": round(ingest_gbps, 2), "ingest_bytes_per_sig": ingest_bytes},
-            "cpu_baseline": cpu,
         }
+    if args.full:
+        more = full_legs(args, cfg, rank, n, chunk, msg_sz, batch, v, step, whole, sync_all, codes, gcodes, c)
+        if rank == 0:
+            out.update(more)
     for vv in ctxs + [v]:
         vv.close()
-    if cfg == "c2" and not args.no_c4:
+    if cfg == "c2" and args.full and not args.no_c4:
         # config 4, the north star's workload (the verify tile's frags), as a
         # sub-object of the same line: every rank runs it after the C2 leg
         c4 = run_c4(args, rank, world, local, dist, emit_line=False)
@@ -545,7 +606,7 @@ def main():
             out["c4"] = {k: c4[k] for k in ("value", "unit", "ms_per_step", "steps", "frags_per_s", "config",
                                             "frag_outcomes_last_batch", "batch_gpu_ms", "batch_host_ms",
                                             "roofline", "ingest_roofline", "pcie_inclusive", "cpu_baseline")}
-    if cfg == "c2" and not args.no_tile and rank == 0 and world == 1:
+    if cfg == "c2" and args.full and not args.no_tile and rank == 0 and world == 1:
         out["tile"] = run_tile_leg(args)
         cb = (out.get("c4") or {}).get("cpu_baseline")
         if cb and cb.get("value"):               # the same C4 workload through the reference's own CPU tile
@@ -589,7 +650,7 @@ def run_tile_leg(args):
     share (oracle/_ref/libfdref_txn.so ref_verify_tile_digest).  prelaid: the
     round-5 headline, kept as a secondary field: flow-controlled on a link
     deep enough to hold the stream.  Binaries are built from the reference
-    sources in the build container (integration/_build); without them the
+    sources in the build container (oracle/_ref/integration); without them the
     leg reports why and the line goes on."""
     sys.path.insert(0, os.path.join(REPO, "tools"))
     sys.path.insert(0, os.path.join(REPO, "tests"))
@@ -600,7 +661,7 @@ def run_tile_leg(args):
         import svc_link_sweep as SL
         import tile_bench as TB
         if not (os.path.exists(SB.EXE) and os.path.exists(SB.SVC)):
-            return {"value": None, "error": "integration/_build/svc_tile_run or svc_run missing (build() with /root/reference)"}
+            return {"value": None, "error": "oracle/_ref/integration/svc_tile_run or svc_run missing (build() with the reference sources)"}
         # the reference's default verify_tile_count (default.toml:776); FD_BENCH_TILE_TILES=3 is round 6's
         # earlier shape (profiles/r06/final)
         tiles = int(os.environ.get("FD_BENCH_TILE_TILES", "6"))
@@ -894,7 +955,7 @@ def run_c4(args, rank, world, local, dist, emit_line=True):
     run(max(args.warmup, 1))
     elapsed, sigs, frags, outs, gpu_ms, host_ms, my_sigs = timed(args.steps)
     pcie = None
-    if frags_mode:
+    if frags_mode and args.full:
         h2d[0] = True
         run(1)
         k2 = args.c4_pcie_steps or args.steps
@@ -912,22 +973,25 @@ def run_c4(args, rank, world, local, dist, emit_line=True):
                         "; per-frag results D2H as in the resident leg; the out dcache stays in HBM"}
         h2d[0] = False
     res = np.concatenate([o[-1][0] for o in outs])
+    if args.dump_outputs and rank == 0 and emit_line:     # the last timed step: every tile's per-frag results and sizes
+        dump_outputs(args.dump_outputs, {"frag_results": res, "txn_sz": np.concatenate([o[-1][2] for o in outs])})
     gpu_ms = [x for g in gpu_ms for x in g]; host_ms = [x for h in host_ms for x in h]
-    # kernel roofline: one extra (untimed) batch of tile 0 with per-kernel HIP-event timing
-    v.set_timing(True)
-    tiles[0].set_ingest_timing(frags_mode)
-    submit(0); tiles[0].complete()
-    prep_ms, dsm_ms, launches = v.get_timing()
-    dsm_units = v.get_dsm_units()
-    ing = tiles[0].ingest_stats() if frags_mode else None
-    tiles[0].set_ingest_timing(False)
-    v.set_timing(False)
+    if args.full:
+        # kernel roofline: one extra (untimed) batch of tile 0 with per-kernel HIP-event timing
+        v.set_timing(True)
+        tiles[0].set_ingest_timing(frags_mode)
+        submit(0); tiles[0].complete()
+        prep_ms, dsm_ms, launches = v.get_timing()
+        dsm_units = v.get_dsm_units()
+        ing = tiles[0].ingest_stats() if frags_mode else None
+        tiles[0].set_ingest_timing(False)
+        v.set_timing(False)
+        launches = max(launches, 1)
     n_sig_batch = int(my_sigs) // max(args.steps, 1)
-    launches = max(launches, 1)
     out = None
     if rank == 0:
         cpu = None
-        if not args.no_cpu_baseline:          # rank 0, after every rank's timed region
+        if args.full and not args.no_cpu_baseline:          # rank 0, after every rank's timed region
             k = min(32768, s.n)
             hi = int((s.off[:k].astype(np.int64) + s.sz[:k]).max())
             threads = max(1, min(args.cpu_threads, os.cpu_count() or 1))
@@ -935,8 +999,6 @@ def run_c4(args, rank, world, local, dist, emit_line=True):
                                     args.cpu_seconds, seed_base, depth)
         counts = {int(a): int(b) for a, b in zip(*np.unique(res, return_counts=True))}
         names = {0: "publish", -1: "verify_fail", -2: "dedup", -3: "parse_fail", -4: "bundle_peer_fail"}
-        dsm_avg = dsm_ms / launches
-        achieved = dsm_units / launches * W_DSM / (dsm_avg * 1e-3) / 1e12
         out = {
             "metric": METRIC,
             "value": round(sigs / elapsed, 1),
@@ -960,17 +1022,22 @@ def run_c4(args, rank, world, local, dist, emit_line=True):
             "frag_outcomes_last_batch": {names[k]: v_ for k, v_ in counts.items()},
             "batch_gpu_ms": round(float(np.median(gpu_ms)), 4),
             "batch_host_ms": round(float(np.median(host_ms)), 4),
-            "roofline": dict(c4_issue_roofline(dsm_avg, dsm_units / launches) or {}, **{
-                         "kernel": "k_verify_dsm", "traffic": None, "units_per_launch": round(dsm_units / launches),
-                         "ref_work_rate_vs_peak": round(achieved / (PEAK_OPS / 1e12), 4),
-                         "avg_launch_ms": round(dsm_avg, 4), "launches_per_batch": launches,
-                         "prep_ms_per_batch": round(prep_ms, 4),
-                         "timing_leg": "one extra batch of tile 0 alone, HIP events around each launch"}),
             "ingest": args.c4_ingest,
-            "ingest_roofline": ingest_roofline(ing),
-            "pcie_inclusive": pcie,
-            "cpu_baseline": cpu,
         }
+        if args.full:
+            dsm_avg = dsm_ms / launches
+            achieved = dsm_units / launches * W_DSM / (dsm_avg * 1e-3) / 1e12
+            out.update({
+                "roofline": dict(c4_issue_roofline(dsm_avg, dsm_units / launches) or {}, **{
+                             "kernel": "k_verify_dsm", "traffic": None, "units_per_launch": round(dsm_units / launches),
+                             "ref_work_rate_vs_peak": round(achieved / (PEAK_OPS / 1e12), 4),
+                             "avg_launch_ms": round(dsm_avg, 4), "launches_per_batch": launches,
+                             "prep_ms_per_batch": round(prep_ms, 4),
+                             "timing_leg": "one extra batch of tile 0 alone, HIP events around each launch"}),
+                "ingest_roofline": ingest_roofline(ing),
+                "pcie_inclusive": pcie,
+                "cpu_baseline": cpu,
+            })
         if emit_line:
             emit(out)
     for tl in tiles:

@@ -5,8 +5,8 @@
      fec_run <out.bin> [sets] [seed] [window]
 
    integration/Makefile builds it twice from the same sources:
-     _build/fec_run_ref   the patch with FD_HAS_HIP off: the reference's add_shred
-     _build/fec_run       FD_HAS_HIP: the engine attached (fd_fec_resolver_hip_attach),
+     oracle/_ref/integration/fec_run_ref   the patch with FD_HAS_HIP off: the reference's add_shred
+     oracle/_ref/integration/fec_run       FD_HAS_HIP: the engine attached (fd_fec_resolver_hip_attach),
                           every window of shreds handed to fd_fec_resolver_hip_preverify
                           before add_shred takes them one at a time
    Both write one record per shred -- add_shred's return value and, for a
@@ -29,7 +29,7 @@
    equal), and reports the resolver's table hits (add_shred took the GPU's
    code) and core verifies.
 
-     _build/fec_run_svc   FD_HAS_HIP_SVC: no HIP in the process; the resolver
+     oracle/_ref/integration/fec_run_svc   FD_HAS_HIP_SVC: no HIP in the process; the resolver
                           is a client of the GPU tile's service
                           (fd_fec_resolver_hip_attach_svc, integration/svc_client.h:
                           SVC_CLIENT_SHM names the run, svc_tile_run host or

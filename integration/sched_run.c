@@ -18,7 +18,7 @@
             packed into pinned buffers and verified by
             fd_replay_hip_txn_verify_host on the GPU, polled without blocking
      svc    the bulk path as the replay tile runs it in service mode
-            (FD_HAS_HIP_SVC, _build/sched_run_svc): claimed batches become
+            (FD_HAS_HIP_SVC, oracle/_ref/integration/sched_run_svc): claimed batches become
             the GPU tile's signature records (include/fd_replay_svc.h) --
             no HIP in this process; a client of the run named by
             SVC_CLIENT_SHM (integration/svc_client.h)

@@ -14,7 +14,7 @@ import subprocess
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-BUILD = os.path.join(os.path.dirname(HERE), "integration", "_build")
+BUILD = os.path.join(os.path.dirname(HERE), "oracle", "_ref", "integration")
 REC_DTYPE = np.dtype([("sig0", "u1", (64,)), ("result", "<i4"), ("source", "u1"), ("_pad", "u1", (3,))])
 assert REC_DTYPE.itemsize == 72
 

@@ -14,7 +14,7 @@ import xxhash
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "tools"))
-BUILD = os.path.join(REPO, "integration", "_build")
+BUILD = os.path.join(REPO, "oracle", "_ref", "integration")
 MOCK = os.path.join(REPO, "oracle", "_ref", "svc_mock")
 DIGEST0 = 0x5eedd16e57
 
@@ -53,7 +53,7 @@ def share_stream(path, s, bid, t, tiles, seed, depth):
 
 def run(stream, tiles, in_depth, logdir, env=None, svc_env=None, mock=False, timeout=240):
     import svc_bench as SB
-    assert os.path.exists(SB.EXE), "integration/_build/svc_tile_run missing: run build() with /root/reference"
+    assert os.path.exists(SB.EXE), "oracle/_ref/integration/svc_tile_run missing: run build() with the reference sources"
     env = dict(env or {}, SVC_RUN_DIGEST="1")                 # the consumers read and digest every frag
     return SB.run_one(stream, tiles, in_depth, timeout, logdir, env=env, svc_env=svc_env,
                       svc_exe=MOCK if mock else None)

@@ -1,7 +1,7 @@
 """GPU: the shred FEC resolver with integration/fd_fec_resolver_hip.patch and
-the engine attached (integration/fec_run.c, _build/fec_run) against the
+the engine attached (integration/fec_run.c, oracle/_ref/integration/fec_run) against the
 same resolver built without FD_HAS_HIP -- the reference's add_shred
-(_build/fec_run_ref) -- on streams the reference's own shredder makes:
+(oracle/_ref/integration/fec_run_ref) -- on streams the reference's own shredder makes:
 wrong-key slots, corrupted signatures, a corrupted shred per 11th set,
 dropped parity shreds, shuffled windows.
 
@@ -22,11 +22,11 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(REPO, "integration", "_build")
+BUILD = os.path.join(REPO, "oracle", "_ref", "integration")
 
 
 def _run(tmp_path, exe, sets, seed, window, name):
-    assert os.path.exists(os.path.join(BUILD, exe)), "integration/_build missing: run build() with /root/reference"
+    assert os.path.exists(os.path.join(BUILD, exe)), "oracle/_ref/integration missing: run build() with the reference sources"
     out = str(tmp_path / name)
     p = subprocess.run([os.path.join(BUILD, exe), out, str(sets), str(seed), str(window)], capture_output=True,
                        text=True, timeout=300)

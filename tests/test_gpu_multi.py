@@ -62,13 +62,13 @@ def test_two_ranks_shard_and_gather(tmp_path):
 
 @pytest.mark.gpu
 def test_bench_world2_default_line_gloo():
-    """The default bench line (C2 leg + the c4 sub-object) at world 2, as the
+    """The --full bench line (C2 leg + the c4 sub-object) at world 2, as the
     driver's scaling runs launch it (gloo here: two ranks on one GPU):
     one JSON line, both legs' values present, the c4 leg's signatures
     summed over the ranks."""
     port = _free_port()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-           "--master-addr", "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2",
+           "--master-addr", "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2", "--full",
            "--sigs", str(1 << 18), "--txns", str(1 << 16), "--steps", "2", "--warmup", "1",
            "--c4-pcie-steps", "1", "--dist-backend", "gloo", "--no-cpu-baseline", "--no-tile"]
     r = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True, timeout=300)
@@ -95,7 +95,7 @@ def test_bench_world2_c5_gloo(tmp_path):
     from firedancer_amd.workload import make_batch_gpu_range
     prefix = str(tmp_path / "codes")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-           "--master-addr", "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2",
+           "--master-addr", "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2", "--full",
            "--config", "c5", "--sigs", str(1 << 21), "--steps", "2", "--warmup", "1",
            "--dist-backend", "gloo", "--cpu-seconds", "1", "--dump-codes", prefix]
     r = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True, timeout=300)

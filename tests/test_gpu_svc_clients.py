@@ -8,7 +8,7 @@ include/fd_replay_svc.h): no HIP in their processes.  VERDICT r05, next #4.
 
 - FEC roots, windows of 64, 512 and 4096 shreds: every shred's add_shred
   outcome and every completed set byte-equal to the reference resolver's
-  (_build/fec_run_ref); every root's verdict equals the reference's
+  (oracle/_ref/integration/fec_run_ref); every root's verdict equals the reference's
   fd_ed25519_verify; add_shred takes the service's verdict for almost every
   first shred; the client is one thread with no device fd.
 - Replay, 16384-txn GPU-signed blocks: every transaction's result equals

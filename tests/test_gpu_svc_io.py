@@ -13,7 +13,7 @@ import subprocess
 import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PROBE = os.path.join(REPO, "integration", "_build", "svc_probe")
+PROBE = os.path.join(REPO, "oracle", "_ref", "integration", "svc_probe")
 
 pytestmark = pytest.mark.gpu
 
@@ -21,7 +21,7 @@ pytestmark = pytest.mark.gpu
 @pytest.mark.parametrize("mode", ["launch", "io"])
 def test_probe_steps(mode):
     if not os.path.exists(PROBE):
-        pytest.skip("integration/_build/svc_probe not built (build() with /root/reference)")
+        pytest.skip("oracle/_ref/integration/svc_probe not built (build() with the reference sources)")
     env = dict(os.environ, FD_VERIFY_SVC_IO=mode)
     r = subprocess.run(["timeout", "-k", "5", "40", PROBE, "64"], capture_output=True, text=True, env=env)
     out = r.stdout + r.stderr

@@ -44,7 +44,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tools"))
 @pytest.fixture(scope="module")
 def stream(tmp_path_factory, verifier):
     import tile_bench as TB
-    assert os.path.exists(os.path.join(TB.BUILD, "tile_run")), "integration/_build missing: run build()"
+    assert os.path.exists(os.path.join(TB.BUILD, "tile_run")), "oracle/_ref/integration missing: run build()"
     p = str(tmp_path_factory.mktemp("tile_run") / "stream.bin")
     s = TB.make_stream(1 << 18, p, seed=0x7e60)
     return p, s

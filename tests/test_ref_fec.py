@@ -9,7 +9,7 @@ exactly its own three inputs and verifies anything else on its core.
 - Without FD_HAS_HIP the patched resolver preprocesses to the reference's
   own token stream: the patch is inert in a reference build.
 - With FD_HAS_HIP it compiles against the reference headers under
-  -Wall -Wextra -Werror (integration/Makefile: _build/fec_strict.o).
+  -Wall -Wextra -Werror (integration/Makefile: oracle/_ref/integration/fec_strict.o).
 - integration/fec_run.c feeds the resolver a stream the reference's
   shredder makes (wrong-key slots, corrupted signatures, one corrupted shred
   per 11th set, dropped parity, shuffled windows): the stream is
@@ -25,7 +25,7 @@ import subprocess
 import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(REPO, "integration", "_build")
+BUILD = os.path.join(REPO, "oracle", "_ref", "integration")
 REF = "/root/reference"
 FEC_TMP = "/tmp/fd_fec_patched_run"
 FLAGS = ["-std=c17", "-D_GNU_SOURCE", "-DFD_HAS_HOSTED=1", "-DFD_HAS_INT128=1", "-DFD_HAS_DOUBLE=1",

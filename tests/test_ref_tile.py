@@ -148,19 +148,19 @@ def test_topology_patch_applies_and_only_unpolls_quic_verify(tmp_path):
 def test_gpu_tile_compiles_against_reference_headers():
     """integration/fd_verify_gpu_tile.c (the topology's vgpu tile and the
     verify_svc object callbacks) under -Wall -Wextra -Werror"""
-    obj = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "integration", "_build",
+    obj = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "integration",
                        "verify_gpu_tile.o")
     if not os.path.exists(obj):
-        pytest.skip("integration/_build missing")
+        pytest.skip("oracle/_ref/integration missing")
     syms = subprocess.run(["nm", obj], capture_output=True, text=True).stdout
     for s_ in ("fd_tile_verify_gpu", "fd_obj_cb_verify_svc", "fd_verify_svc_boot", "fd_verify_svc_poll"):
         assert s_ in syms, s_
 
 
 def test_tile_run_uses_range_entry_points():
-    exe = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "integration", "_build", "tile_run")
+    exe = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "integration", "tile_run")
     if not os.path.exists(exe):
-        pytest.skip("integration/_build missing")
+        pytest.skip("oracle/_ref/integration missing")
     syms = subprocess.run(["nm", "-u", exe], capture_output=True, text=True).stdout
     for s_ in ("fd_verify_hip_tile_submit_range", "fd_verify_hip_tile_complete_range"):
         assert s_ in syms, s_
@@ -171,10 +171,10 @@ def test_patched_tile_compiles_warning_free():
     (both patches' tile side, range mode included) and tile_run.c under
     -Wall -Wextra -Werror (the populate_allowed_* hooks excepted: tile_run
     drives the callbacks itself)."""
-    obj = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "integration", "_build",
+    obj = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "integration",
                        "tile_run_strict.o")
     if not os.path.exists(obj):
-        pytest.skip("integration/_build missing")
+        pytest.skip("oracle/_ref/integration missing")
     syms = subprocess.run(["nm", obj], capture_output=True, text=True).stdout
     for s_ in ("fd_verify_hip_tile_submit_range", "fd_verify_hip_tile_complete_range",
                "fd_verify_hip_tile_set_staging", "fd_verify_hip_tile_submit_frags"):

@@ -11,7 +11,7 @@ sandbox -- as the verify tiles do:
 - the FEC resolver with integration/fd_fec_resolver_hip.patch in service
   mode (fd_fec_resolver_hip_attach_svc; integration/fec_run.c built with
   FD_HAS_HIP_SVC) gives every shred the reference add_shred's outcome and
-  every completed set byte for byte (the same file as _build/fec_run_ref),
+  every completed set byte for byte (the same file as oracle/_ref/integration/fec_run_ref),
   takes the service's verdict for almost every first shred, and runs as one
   thread with no device fd;
 - the replay scheduler with integration/fd_replay_hip.patch, its claimed
@@ -100,7 +100,7 @@ def test_replay_svc_bad_signature_kills_the_block(replay_runs):
 
 
 def test_replay_tile_service_mode_has_no_hip():
-    """integration/fd_replay_hip.patch with FD_HAS_HIP_SVC (_build/replay_tile_svc.o,
+    """integration/fd_replay_hip.patch with FD_HAS_HIP_SVC (oracle/_ref/integration/replay_tile_svc.o,
     -Wall -Wextra -Werror): the replay tile claims batches and joins the
     service as a client, and references nothing of the engine -- it keeps
     the reference's seccomp policy and fd list (its populate_allowed_*

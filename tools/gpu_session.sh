@@ -8,8 +8,8 @@
 # Steps (arguments after ':' are passed on, ',' separates them, '+' stands for
 # a ',' inside one argument: --tiles,1+2+4 is --tiles 1,2,4):
 #   tests[:files]      pytest -m gpu on the given test files (default: all)
-#   bench[:args]       python bench.py <args>                  -> bench_<n>.json
-#   c4[:args]          python bench.py --config c4 <args>       -> c4_<n>.json
+#   bench[:args]       python bench.py --full <args>           -> bench_<n>.json
+#   c4[:args]          python bench.py --full --config c4 <args> -> c4_<n>.json
 #   ab[:ENV=V,...]     C4 bench with extra environment (A/B)    -> ab_<n>.json
 #   stats[:args]       rocprofv3 --kernel-trace --stats of bench.py --contexts 1 <args>
 #   c4stats[:args]     the same over the C4 bench (one tile, serialised dispatches)
@@ -25,7 +25,7 @@
 #   smoke              __graft_entry__.smoke()
 #   svc[:args]         python tools/svc_bench.py <args>         -> svc_<n>.jsonl (the service-mode stage)
 #   sweep[:args]       python tools/svc_link_sweep.py <args>    -> sweep_<n>.jsonl, table in sweep_<n>.err
-#   env:K=V,...        export K=V for the steps after it (e.g. SVC_BENCH_TILE_EXE=integration/_build/svc_tile_run_d2)
+#   env:K=V,...        export K=V for the steps after it (e.g. SVC_BENCH_TILE_EXE=oracle/_ref/integration/svc_tile_run_d2)
 # Round-5 service sessions, as steps (their one-off scripts tools/r05*_session.sh are in git history):
 #   the DSM reserve A/B (r05aq): svc:--frags,4194304,--tiles,2+3,--repeat,2,--prelay,--env,SVC_RUN_REQ_DEPTH=8
 #                                svc:...,--svc-env,FD_ED25519_HIP_DSM_RESERVE=192
@@ -67,33 +67,33 @@ for step in "$@"; do
           -p no:cacheprovider > $O/pytest_$n.txt 2>&1 || fail tests $? $O/pytest_$n.txt
       tail -3 $O/pytest_$n.txt ;;
     bench)
-      timeout -k 10 600 python bench.py $a > $O/bench_$n.json 2> $O/bench_$n.err || fail bench $? $O/bench_$n.err
+      timeout -k 10 600 python bench.py --full $a > $O/bench_$n.json 2> $O/bench_$n.err || fail bench $? $O/bench_$n.err
       cut -c1-400 $O/bench_$n.json ;;
     c4)
-      timeout -k 10 900 python bench.py --config c4 $a > $O/c4_$n.json 2> $O/c4_$n.err || fail c4 $? $O/c4_$n.err
+      timeout -k 10 900 python bench.py --full --config c4 $a > $O/c4_$n.json 2> $O/c4_$n.err || fail c4 $? $O/c4_$n.err
       python3 -c "import json,sys; d=json.load(open('$O/c4_$n.json')); print('c4', d['value'], (d.get('pcie_inclusive') or {}).get('value'), d.get('batch_gpu_ms'))" ;;
     ab)
-      timeout -k 10 900 env $a python bench.py --config c4 --no-cpu-baseline --c4-pcie-steps 4 \
+      timeout -k 10 900 env $a python bench.py --full --config c4 --no-cpu-baseline --c4-pcie-steps 4 \
           > $O/ab_$n.json 2> $O/ab_$n.err || fail ab $? $O/ab_$n.err
       python3 -c "import json; d=json.load(open('$O/ab_$n.json')); print('ab [$a]', d['value'], d.get('batch_gpu_ms'))" ;;
     stats)
       timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$n -o run -- \
-          python3 bench.py --contexts 1 --no-c4 $a > $O/stats_$n.json 2> $O/stats_$n.err || fail stats $? $O/stats_$n.err
+          python3 bench.py --full --contexts 1 --no-c4 $a > $O/stats_$n.json 2> $O/stats_$n.err || fail stats $? $O/stats_$n.err
       echo "stats ok" ;;
     c4stats)
       timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/c4stats_$n -o run -- \
-          python3 bench.py --config c4 --tiles 1 --no-cpu-baseline --steps 3 --warmup 1 --c4-pcie-steps 1 $a \
+          python3 bench.py --full --config c4 --tiles 1 --no-cpu-baseline --steps 3 --warmup 1 --c4-pcie-steps 1 $a \
           > $O/c4stats_$n.json 2> $O/c4stats_$n.err || fail c4stats $? $O/c4stats_$n.err
       echo "c4stats ok" ;;
     pmc)
-      B="python3 bench.py --contexts 1 --no-c4 --no-cpu-baseline --steps 2 --warmup 1"
+      B="python3 bench.py --full --contexts 1 --no-c4 --no-cpu-baseline --steps 2 --warmup 1"
       pmc_pass pmc_valu "$VALU_G" $B
       pmc_pass pmc_sq "$SQ_G" $B
       pmc_pass pmc_fetch "FETCH_SIZE" $B
       pmc_pass pmc_write "WRITE_SIZE" $B
       pmc_pass pmc_tcc "TCC_HIT_sum TCC_MISS_sum GRBM_GUI_ACTIVE GRBM_COUNT" $B ;;
     c4pmc)
-      B="python3 bench.py --config c4 --tiles 1 --no-cpu-baseline --steps 2 --warmup 1 --c4-pcie-steps 1 $a"
+      B="python3 bench.py --full --config c4 --tiles 1 --no-cpu-baseline --steps 2 --warmup 1 --c4-pcie-steps 1 $a"
       pmc_pass c4pmc_valu "$VALU_G" $B
       pmc_pass c4pmc_fetch "FETCH_SIZE" $B
       pmc_pass c4pmc_write "WRITE_SIZE" $B ;;
@@ -108,12 +108,12 @@ for step in "$@"; do
       bash tools/run_profile.sh $T || fail profile $?
       bash tools/run_valu_calib.sh $T || fail valu $?
       bash tools/run_c4_issue.sh $T || fail c4issue $?
-      B="python3 bench.py --config c4 --tiles 1 --no-cpu-baseline --steps 2 --warmup 1 --c4-pcie-steps 1"
+      B="python3 bench.py --full --config c4 --tiles 1 --no-cpu-baseline --steps 2 --warmup 1 --c4-pcie-steps 1"
       pmc_pass c4pmc_valu "$VALU_G" $B
       pmc_pass c4pmc_fetch "FETCH_SIZE" $B
       pmc_pass c4pmc_write "WRITE_SIZE" $B
       timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/c4stats_$n -o run -- \
-          python3 bench.py --config c4 --tiles 1 --no-cpu-baseline --steps 3 --warmup 1 --c4-pcie-steps 1 \
+          python3 bench.py --full --config c4 --tiles 1 --no-cpu-baseline --steps 3 --warmup 1 --c4-pcie-steps 1 \
           > $O/c4stats_$n.json 2> $O/c4stats_$n.err || fail c4stats $? $O/c4stats_$n.err
       echo "profile set ok" ;;
     svc)

@@ -9,6 +9,6 @@ export TMPDIR=/tmp
 R=$(pwd); T=${1:-r03}; O=$R/gpurun_out/c4issue_$T; mkdir -p $O
 G="SQ_INSTS_VALU SQ_THREAD_CYCLES_VALU SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_VALU2 SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 SQ_BUSY_CYCLES SQ_WAVES GRBM_GUI_ACTIVE GRBM_COUNT"
 timeout -s KILL 300 rocprofv3 --pmc $G --kernel-trace --output-format csv -d $O/engine -o run -- \
-    python3 bench.py --config c4 --no-cpu-baseline --steps 2 --warmup 1 --c4-pcie-steps 1 > $O/bench.json 2> $O/engine.err
+    python3 bench.py --full --config c4 --no-cpu-baseline --steps 2 --warmup 1 --c4-pcie-steps 1 > $O/bench.json 2> $O/engine.err
 rc=$?; echo "c4 pmc rc=$rc"; [ $rc -ne 0 ] && { tail -5 $O/engine.err; exit $rc; }
 exit 0

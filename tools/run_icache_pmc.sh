@@ -8,7 +8,7 @@ T=${1:-icache}; shift
 O=$PWD/gpurun_out/$T; mkdir -p $O
 G="SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE SQ_IFETCH SQ_IFETCH_LEVEL SQ_WAIT_INST_ANY SQ_WAVE_CYCLES"
 timeout -s KILL 240 rocprofv3 --pmc $G --kernel-trace --output-format csv -d $O/p -o run -- \
-    python3 bench.py --contexts 1 --no-cpu-baseline --steps 2 --warmup 1 "$@" > $O/out.json 2> $O/err.txt
+    python3 bench.py --full --contexts 1 --no-cpu-baseline --steps 2 --warmup 1 "$@" > $O/out.json 2> $O/err.txt
 rc=$?; echo "icache pass rc=$rc"; [ $rc -ne 0 ] && { tail -5 $O/err.txt; exit $rc; }
 python3 - $O <<'PY'
 import csv, glob, sys, collections

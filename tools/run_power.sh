@@ -4,7 +4,7 @@
 # k_verify_dsm runs at the power cap and that the rate holds over a minute.
 # Usage: bash tools/run_power.sh [tag] [steps]
 O=gpurun_out/${1:-power}; S=${2:-8000}; mkdir -p $O
-timeout -k 10 300 python bench.py --no-cpu-baseline --steps $S --warmup 2 > $O/power_bench.json 2> $O/power_bench.err &
+timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps $S --warmup 2 > $O/power_bench.json 2> $O/power_bench.err &
 B=$!
 sleep 15
 for i in 1 2 3 4 5 6 7 8 9 10; do

@@ -4,7 +4,7 @@
 # Usage: bash tools/run_profile_c4.sh <tag>  -> gpurun_out/prof_c4_<tag>/...
 export TMPDIR=/tmp
 R=$(pwd); T=${1:-r02}; O=$R/gpurun_out/prof_c4_$T; mkdir -p $O
-ARGS="--config c4 --no-cpu-baseline --steps 3 --warmup 1"
+ARGS="--full --config c4 --no-cpu-baseline --steps 3 --warmup 1"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o run -- \
     python3 bench.py $ARGS > $O/bench_stats.json 2> $O/bench_stats.err
 rc=$?; echo "stats rc=$rc"; [ $rc -ne 0 ] && { tail -20 $O/bench_stats.err; exit $rc; }

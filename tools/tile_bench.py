@@ -2,7 +2,7 @@
 """Time the reference's verify tile patched to use the engine (north star's
 operating point), in the reference's own stem loop, on one GPU.
 
-For each configuration: one producer process (integration/_build/tile_run
+For each configuration: one producer process (oracle/_ref/integration/tile_run
 produce: the quic side of the quic_verify link, frags pre-laid in its dcache,
 mcache lines published with flow control) and T verify tile processes
 (tile_run tile: fd_verify_tile.c + integration/fd_verify_tile_hip.patch,
@@ -34,7 +34,7 @@ import numpy as np
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tests"))
-BUILD = os.path.join(REPO, "integration", "_build")
+BUILD = os.path.join(REPO, "oracle", "_ref", "integration")
 # (batch_max, inflight, gpu_copy): the patch's FD_VERIFY_HIP_* settings; gpu_copy 0 is the host
 # during_frag copy ("h" suffix)
 SWEEP = [(b, i, g) for b in (1024, 2048, 4096, 8192) for i in (2, 3, 4) for g in (1, 0)] + \
@@ -65,7 +65,7 @@ def build():
         subprocess.check_call(["make", "-s", "-C", os.path.join(REPO, "integration"), f"VARIANT={v}",
                                f"DEFS=-DFD_VERIFY_HIP_BATCH_MAX={b}UL -DFD_VERIFY_HIP_INFLIGHT={i}UL "
                                f"-DFD_VERIFY_HIP_RANGE_BATCH_MAX={b}UL "
-                               f"-DFD_VERIFY_HIP_GPU_COPY={g}", f"_build/tile_run{v}"])
+                               f"-DFD_VERIFY_HIP_GPU_COPY={g}", f"../oracle/_ref/integration/tile_run{v}"])
         print(binary(b, i, g))
 
 
