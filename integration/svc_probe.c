@@ -1,19 +1,20 @@
-/* svc_probe.c -- the verify service's IO engine step by step, with no tile
-   process: one segment in this process's memory, the service on GPU 0, and
-   requests posted by hand (fd_verify_svc.h's tile-side calls).  Each step
-   prints one line with the service's state (fd_verify_svc_debug) and fails
-   loudly with a deadline, so a run names the step an engine change broke:
+/* svc_probe.c -- the verify service step by step, with no tile process: one
+   segment in this process's memory, the service on GPU 0, and requests
+   posted by hand (fd_verify_svc.h's tile-side calls).  Each step prints one
+   line with the service's state (fd_verify_svc_debug) and fails loudly with
+   a deadline, so a run names the step a change to the service broke:
 
-     idle       the engine runs 0.5 s with nothing posted
-     empty      a frag request with no frags: INGESTED by the engine, RESULTS
+     idle       the service polls 0.5 s with nothing posted
+     empty      a frag request with no frags: RESULTS at once
      frags      a frag request of 64 frags in the frag area: ingested, verified
                 (zero bytes: every frag fails its parse), RESULTS; the tile
                 side frees the slots
      flush      a flush of host-written entries (nothing to copy): flush_done
-     delete     teardown (the engine stopped and drained)
+     latency    32 more frag requests one at a time: post -> INGESTED
+     delete     teardown (every stream drained)
 
    svc_probe [frags]          (default 64)
-   Built by integration/Makefile (svc-probe), run by tests/test_gpu_svc_io.py. */
+   Built by integration/Makefile (svc-probe), run by tests/test_gpu_svc_probe.py. */
 
 #define _GNU_SOURCE
 #include "fd_verify_svc.h"

@@ -57,8 +57,8 @@ static svc_run_hdr_t * svc_hdr;
 static int             hdr_sandboxed;
 
 /* SIGTERM (the driver's timeout): leave the poll loop and tear the service
-   down -- the IO engine stopped and drained -- rather than die with a
-   kernel running on the GPU */
+   down -- every stream drained -- rather than die with a kernel running on
+   the GPU */
 static volatile int svc_term;
 static void svc_sigterm( int sig ) { (void)sig; svc_term = 1; }
 static void

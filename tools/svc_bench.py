@@ -184,7 +184,7 @@ def run_one(stream, tiles, in_depth, timeout, logdir, env=None, svc_env=None, sv
                 res["clients_lines"][cname] = lines
         return res
     finally:
-        # the GPU tile first, with SIGTERM: it stops its IO engine and drains the GPU before it
+        # the GPU tile first, with SIGTERM: it tears the service down and drains the GPU before it
         # exits (integration/svc_run.c); a process killed with a kernel on the card can leave it faulted
         for n, p in procs:
             if n == "svc" and p.poll() is None:

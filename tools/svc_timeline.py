@@ -7,8 +7,9 @@ usage: python tools/svc_timeline.py <svc_kernel_trace.csv[.gz]> > timeline.json
 A verify launch is the kernels of one launch stream from k_svc_assemble to
 k_svc_results.  For each launch: frags (k_svc_assemble's grid), start, end,
 the phases (txn kernel, prep, DSM), the DSM's ns per frag, and the share of
-the DSM's time a gather (k_svc_gather) or flush (k_svc_compact) ran beside
-it.  Run-level: the gaps with no verify kernel, what ran in them, how many
+the DSM's time a gather (k_svc_gather*) or flush (k_svc_compact*; by prefix:
+earlier rounds' traces name k_svc_gather_wave and k_svc_compact_batch) ran
+beside it.  Run-level: the gaps with no verify kernel, what ran in them, how many
 launches overlapped, and the DSM ns per frag against the gather overlap
 (split at the median) -- whether sharing the GPU with the PCIe kernels
 slows the DSM."""
@@ -55,8 +56,8 @@ def union(iv):
 
 def main():
     rows = load(sys.argv[1])
-    gat = union([(r["s"], r["e"]) for r in rows if r["k"] == "k_svc_gather" and r["g"] > 256])
-    fl = union([(r["s"], r["e"]) for r in rows if r["k"] == "k_svc_compact" and r["g"] > 256])
+    gat = union([(r["s"], r["e"]) for r in rows if r["k"].startswith("k_svc_gather") and r["g"] > 256])
+    fl = union([(r["s"], r["e"]) for r in rows if r["k"].startswith("k_svc_compact") and r["g"] > 256])
     launches, open_ = [], {}
     for r in rows:
         q = r["q"]

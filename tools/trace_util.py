@@ -6,8 +6,10 @@ large).
 usage: python tools/trace_util.py <dir with *kernel_trace.csv> > util.json
 
 Classes: verify (k_txnm_batch, k_verify_prep, k_verify_dsm, the reduces,
-k_msg_order, k_svc_assemble, k_svc_results), ingest (k_svc_gather), flush
-(k_svc_compact), other.  For each class: the union of its kernels'
+k_msg_order, k_svc_assemble, k_svc_results), ingest (k_svc_gather*), flush
+(k_svc_compact*; by prefix, so that traces of earlier rounds, whose kernels
+were k_svc_gather_wave and k_svc_compact_batch, classify too), other.  For
+each class: the union of its kernels'
 [start, end) intervals (the time at least one ran) and the summed kernel
 time; for pairs, the time both ran at once; the span from the first
 kernel's start to the last one's end, within the run (first real ingest
@@ -26,8 +28,9 @@ VERIFY = ("k_txnm_batch", "k_verify_prep", "k_verify_dsm", "k_seg_reduce", "k_gr
 
 def klass(name):
     base = name.split("(")[0].split()[-1].split("<")[0]
-    if base in CLASSES:
-        return CLASSES[base]
+    for prefix, c in CLASSES.items():
+        if base.startswith(prefix):
+            return c
     return "verify" if base in VERIFY else "other"
 
 
