@@ -13,8 +13,8 @@ CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libfd_ed25519_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 SOURCES = ["fd_ed25519_hip.hip", "fd_ed25519_dev.h", "fd_hip_order.h", "fd_txn_hip.hip", "fd_txn_hip_int.h", "fd_sha512_hip.hip",
-           "fd_verify_svc.hip"]
-UNITS = ["fd_ed25519_hip.hip", "fd_txn_hip.hip", "fd_sha512_hip.hip", "fd_verify_svc.hip"]
+           "fd_verify_svc.hip", "fd_shred_hip.hip", "fd_sha256_dev.h"]
+UNITS = ["fd_ed25519_hip.hip", "fd_txn_hip.hip", "fd_sha512_hip.hip", "fd_verify_svc.hip", "fd_shred_hip.hip"]
 
 
 def _stale(target, deps):

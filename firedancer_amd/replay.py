@@ -9,6 +9,10 @@ Reference interfaces mirrored:
                            per txn by the exec tile (fd_exec_tile.c:161)
   FEC-set root check       src/disco/shred/fd_fec_resolver.c:476
                            (fd_ed25519_verify of a 32-B Merkle root)
+  fd_shred_merkle_root     src/ballet/shred/fd_shred.c:108-131 (the root of
+                           each raw shred, and with it the FEC-set check from
+                           the shreds themselves: shred_roots_dev,
+                           ShredVerifier)
   fd_precompile_ed25519_verify
                            src/flamenco/runtime/program/fd_precompiles.c:114-211
                            (ed25519 program instructions: offset records naming
@@ -31,7 +35,11 @@ FD_RUNTIME_TXN_ERR_SIGNATURE_FAILURE = -13
 EXPORTS = ("fd_replay_hip_new", "fd_replay_hip_delete", "fd_replay_hip_txn_verify_dev", "fd_replay_hip_poll",
            "fd_replay_hip_txn_verify_host", "fd_replay_hip_wait",
            "fd_fec_hip_verify_roots_dev", "fd_precompile_hip_new", "fd_precompile_hip_delete",
-           "fd_precompile_hip_ed25519_verify_dev")
+           "fd_precompile_hip_ed25519_verify_dev",
+           "fd_shred_hip_new", "fd_shred_hip_delete", "fd_shred_hip_roots_dev", "fd_shred_hip_verify_dev",
+           "fd_shred_hip_stats", "fd_sha256_hip_batch_dev")
+
+FD_SHRED_HIP_NO_ROOT = 1   # code of a shred without a root (include/fd_replay_hip.h)
 
 # fd_executor_err.h:14,40 and fd_precompiles.h:16-18
 FD_EXECUTOR_INSTR_SUCCESS = 0
@@ -82,6 +90,16 @@ def lib():
         L.fd_precompile_hip_delete.argtypes = [vp]
         L.fd_precompile_hip_ed25519_verify_dev.restype = c.c_int
         L.fd_precompile_hip_ed25519_verify_dev.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp]
+        L.fd_shred_hip_new.restype = vp
+        L.fd_shred_hip_new.argtypes = [vp, u64]
+        L.fd_shred_hip_delete.argtypes = [vp]
+        L.fd_shred_hip_roots_dev.restype = c.c_int
+        L.fd_shred_hip_roots_dev.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp]
+        L.fd_shred_hip_verify_dev.restype = c.c_int
+        L.fd_shred_hip_verify_dev.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.fd_shred_hip_stats.argtypes = [vp, c.POINTER(u64)]
+        L.fd_sha256_hip_batch_dev.restype = c.c_int
+        L.fd_sha256_hip_batch_dev.argtypes = [vp, u64, vp, vp, vp, vp, vp]
         _bound = True
     return L
 
@@ -164,6 +182,81 @@ def fec_verify_roots_dev(verifier, n, roots, sigs, pubs, codes, stream=None):
             _ptr(sigs, 64 * n, "sigs", dev), _ptr(pubs, 32 * n, "pubs", dev), _ptr(codes, n, "codes", dev))
     with verifier._stream(stream) as h:
         return lib().fd_fec_hip_verify_roots_dev(*args, h)
+
+
+def _shred_args(n, pool, off, sz, roots, flags, dev):
+    return (_ptr(pool, 1, "pool", dev), _ptr(off, 4 * n, "off", dev), _ptr(sz, 4 * n, "sz", dev),
+            _ptr(roots, 32 * n, "roots", dev), _ptr(flags, n, "flags", dev))
+
+
+def shred_roots_dev(verifier, n, pool, off, sz, roots, flags, stream=None):
+    """fd_shred_hip_roots_dev: shred i = pool[off[i], +sz[i]) (uint32 off / sz,
+    any byte offset; pool readable to the 16-byte boundary past each shred)
+    -> roots[32i:32i+32] and flags[i] (1: the shred has a root; 0: roots
+    bytes zero).  All GPU tensors on the verifier's device."""
+    n = int(n)
+    args = _shred_args(n, pool, off, sz, roots, flags, verifier.device)
+    with verifier._stream(stream) as h:
+        return lib().fd_shred_hip_roots_dev(verifier.ctx, n, *args, h)
+
+
+def shred_verify_dev(shred_verifier, n, pool, off, sz, pubs, roots, flags, codes, stream=None):
+    """fd_shred_hip_verify_dev on a ShredVerifier: roots and flags as
+    shred_roots_dev, then codes[i] (int8) = fd_ed25519_verify(root, shred
+    signature, pubs[32i:32i+32]) for flagged shreds, verified once per
+    distinct (signature, root, key), FD_SHRED_HIP_NO_ROOT for the others."""
+    return shred_verifier.verify_dev(n, pool, off, sz, pubs, roots, flags, codes, stream)
+
+
+class ShredVerifier:
+    """FEC-set verification from raw shreds, up to n_max shreds per call
+    (fd_shred_hip_t)."""
+
+    def __init__(self, verifier, n_max):
+        self._lib = lib()
+        self.verifier = verifier
+        self.s = self._lib.fd_shred_hip_new(verifier.ctx, int(n_max))
+        if not self.s:
+            raise RuntimeError("fd_shred_hip_new failed")
+        self.n_max = int(n_max)
+
+    def verify_dev(self, n, pool, off, sz, pubs, roots, flags, codes, stream=None):
+        n, dev = int(n), self.verifier.device
+        args = _shred_args(n, pool, off, sz, roots, flags, dev)
+        args = args[:3] + (_ptr(pubs, 32 * n, "pubs", dev),) + args[3:] + (_ptr(codes, n, "codes", dev),)
+        with self.verifier._stream(stream) as h:
+            rc = self._lib.fd_shred_hip_verify_dev(self.s, n, *args, h)
+        if rc:
+            raise ValueError(f"fd_shred_hip_verify_dev: n={n} > n_max={self.n_max}")
+
+    def stats(self):
+        """(shreds with a root, signatures verified) of the last verify_dev,
+        once its stream has passed it."""
+        out = (ctypes.c_ulong * 2)()
+        self._lib.fd_shred_hip_stats(self.s, out)
+        return int(out[0]), int(out[1])
+
+    def close(self):
+        if self.s:
+            self._lib.fd_shred_hip_delete(self.s)
+            self.s = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def sha256_batch_dev(verifier, n, pool, off, sz, out, stream=None):
+    """SHA-256 of n messages pool[off[i], +sz[i]) -> out (32 bytes each), all
+    GPU tensors on the verifier's device (the calling shape of
+    sha512.sha512_batch_dev)."""
+    n, dev = int(n), verifier.device
+    args = (verifier.ctx, n, _ptr(pool, 1, "pool", dev), _ptr(off, 4 * n, "off", dev), _ptr(sz, 4 * n, "sz", dev),
+            _ptr(out, 32 * n, "out", dev))
+    with verifier._stream(stream) as h:
+        return lib().fd_sha256_hip_batch_dev(*args, h)
 
 
 class PrecompileVerifier:

@@ -128,6 +128,89 @@ fd_fec_hip_verify_roots_dev( fd_ed25519_hip_ctx_t * ctx,
                              signed char *          d_codes,
                              void *                 stream );
 
+/* ---- shred Merkle roots and FEC sets from raw shreds ------------------------
+
+   The roots above come from the shreds themselves: fd_shred_merkle_root
+   (src/ballet/shred/fd_shred.c:108-131), one SHA-256 over the
+   Merkle-protected part of the shred and one 66-byte merge per proof level.
+   These entries derive them on the device.  Shred i is
+   d_pool[ d_off[i], +d_sz[i] ), at any byte offset (as shreds lie in a
+   net-link dcache); d_pool stays readable to the 16-byte boundary past each
+   shred.  d_roots (32 n bytes) and d_pubs are 16-byte aligned.
+
+   d_flags[i] is 1 and d_roots + 32 i holds shred i's root iff the resolver's
+   add_shred would derive one (integration/fd_fec_resolver_hip.patch,
+   fec_hip_root): d_sz[i] covers the shred's type (1203 data, 1228 code), the
+   type is one of the six Merkle types, the proof depth d is at most 9, a
+   code shred's data_cnt and code_cnt are in [1,67], the in-type index
+   (idx - fec_set_idx as uint for data, code.idx for code) is below 67 and
+   the tree index (code: code.idx + data_cnt) below 2^d.  Otherwise
+   d_flags[i] is 0, the 32 root bytes are zero and nothing past d_sz[i] is
+   interpreted. */
+
+#define FD_SHRED_HIP_NO_ROOT (1)   /* d_codes of a shred without a root; every FD_ED25519_* code is <= 0 */
+
+typedef struct fd_shred_hip fd_shred_hip_t;
+
+/* device scratch for n_max shreds per call on ctx's device (reserves n_max
+   signatures of verify scratch in ctx) */
+fd_shred_hip_t * fd_shred_hip_new   ( fd_ed25519_hip_ctx_t * ctx, ulong n_max );
+void             fd_shred_hip_delete( fd_shred_hip_t * s );
+
+/* roots and flags only.  Asynchronous on stream (NULL: ctx's stream).
+   Returns 0 (n 0: nothing launched), or -1 without touching the GPU if n
+   does not fit a uint. */
+int
+fd_shred_hip_roots_dev( fd_ed25519_hip_ctx_t * ctx,
+                        ulong                  n,
+                        uchar const *          d_pool,
+                        uint const *           d_off,
+                        uint const *           d_sz,
+                        uchar *                d_roots,
+                        uchar *                d_flags,
+                        void *                 stream );
+
+/* roots and flags, then one fd_ed25519_verify( root, 32, shred signature,
+   d_pubs + 32 i ) per distinct (signature, root, leader key) triple of the
+   flagged shreds, and d_codes[i] = that verify's code (FD_ED25519_*, in
+   ctx's error mode) for every flagged shred, FD_SHRED_HIP_NO_ROOT for the
+   others: equal triples get equal codes.  d_pubs + 32 i is shred i's slot
+   leader.  One stream-ordered sequence without a host round trip; calls on
+   one handle run in call order and may follow each other without a sync.
+   Returns 0 (n 0: nothing launched), or -1 without touching the GPU if
+   n > n_max. */
+int
+fd_shred_hip_verify_dev( fd_shred_hip_t * s,
+                         ulong            n,
+                         uchar const *    d_pool,
+                         uint const *     d_off,
+                         uint const *     d_sz,
+                         uchar const *    d_pubs,
+                         uchar *          d_roots,
+                         uchar *          d_flags,
+                         signed char *    d_codes,
+                         void *           stream );
+
+/* Of the last fd_shred_hip_verify_dev call, once its stream has passed it
+   (the caller synchronises): out[0] shreds with a root, out[1] signatures
+   verified (distinct triples). */
+void
+fd_shred_hip_stats( fd_shred_hip_t const * s, ulong out[ 2 ] );
+
+/* Plain SHA-256 (src/ballet/sha256/fd_sha256.h) of n messages
+   d_pool[ d_off[i], +d_sz[i] ) to 32-byte digests at d_hash + 32 i (16-byte
+   aligned), with the device core the roots use; d_pool readable to the
+   16-byte boundary past each message.  The calling shape of
+   fd_sha512_hip_batch_dev (fd_sha512_hip.h).  Asynchronous on stream. */
+int
+fd_sha256_hip_batch_dev( fd_ed25519_hip_ctx_t * ctx,
+                         ulong                  n,
+                         uchar const *          d_pool,
+                         uint const *           d_off,
+                         uint const *           d_sz,
+                         uchar *                d_hash,
+                         void *                 stream );
+
 /* ---- ed25519 program (precompile) instructions -----------------------------
 
    fd_precompile_ed25519_verify (fd_precompiles.c:114-211, data fetch
